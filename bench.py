@@ -14,14 +14,21 @@ resident in HBM: grad = (sum over ranks of residual) / N, residual = 0.
   N > 1   RCCL all-reduce over xGMI + one fused kernel (grad /= N, residual = 0);
           --algo selects another schedule (hops, direct, xgmi).
 Every timed step consumes its own pre-generated residual bucket (W + K buckets
-of 256 MiB in HBM), so no step reduces an already-zeroed bucket.
+of 256 MiB in HBM), so no step reduces an already-zeroed bucket — up to 32 GiB
+of buckets; a longer run goes round that pool, the last step keeping a fresh
+bucket of its own (Runner).
+
+A plain run sets up, warms up, times the K steps and prints the line (N = 1:
+with the roofline the timed steps' own event pair gives).  --dump-outputs DIR
+writes what the last timed step returned, for comparing two builds.  --full
+adds the check and every informational object below.
 
 value = N * bucket_bytes * K / max-over-ranks(elapsed) / 2^30: the gradient
 bytes every rank fed into the reduction per second (weak scaling: the bucket
 per GPU is fixed).  algbw_gib_s (bucket / time) and busbw_gib_s
 (algbw * 2(N-1)/N) are reported beside it.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (--full):
   check         the last timed step against the exact average of all N inputs
                 (regenerated on every rank), residual all zero
   roofline      the step's dominant kernel (N = 1: HBM) or exchange (N > 1: xGMI
@@ -74,6 +81,13 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--bucket-mib", type=int, default=256)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: its check against the exact average and every informational leg "
+                         "(roofline passes, other schedules, sizes and precisions, host-fed and TCP rounds, "
+                         "CPU baseline); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (grad, residual) as "
+                         "DIR/<name>.npy, float32; buckets above 4 Mi elements as a fixed seeded sample")
     ap.add_argument("--wire", choices=["f32", "f16"], default="f32")
     ap.add_argument("--algo", choices=["auto", "allreduce", "hops", "direct", "xgmi"], default="auto")
     ap.add_argument("--segments", type=int, default=0,
@@ -1029,29 +1043,40 @@ def tcp_edge(ono_amd, elems: int, rounds: int, ranks: int = 2) -> dict:
 class Runner:
     """W + K pull_grads rounds of a ring, each over its own freshly generated
     bucket already resident in HBM (W + K buckets of the bench size), output
-    into one grad bucket."""
+    into one grad bucket.  The buckets take at most POOL_BYTES of HBM: a run
+    of more steps than that holds goes round the pool (a bucket met again has
+    been zeroed by its earlier round: the same bytes move), except the last
+    step, whose fresh bucket no other step touches — what the last step
+    computes depends on W + K only."""
+
+    POOL_BYTES = 32 << 30
 
     def __init__(self, torch, ono_amd, args, ctl: Ctl, world: int, rank: int, elems: int):
         self.torch, self.ono_amd, self.args, self.ctl = torch, ono_amd, args, ctl
         self.world, self.rank, self.elems = world, rank, elems
         self.nb = args.warmup + args.steps
-        self.residuals = [torch.empty(elems, dtype=torch.float32, device="cuda") for _ in range(self.nb)]
+        self.pool = min(self.nb, max(2, self.POOL_BYTES // (4 * elems)))
+        self.residuals = [torch.empty(elems, dtype=torch.float32, device="cuda") for _ in range(self.pool)]
         self.grad = torch.empty(elems, dtype=torch.float32, device="cuda")
         self.stream = torch.cuda.current_stream()
 
-    def refill(self) -> None:  # a fresh, distinct bucket for every step (untimed)
+    def bucket(self, i: int):
+        """The residual bucket of step i (the last step's is its own)."""
+        return self.residuals[-1] if i == self.nb - 1 else self.residuals[i % max(1, self.pool - 1)]
+
+    def refill(self) -> None:  # a fresh, distinct bucket for every step the pool holds (untimed)
         for i, t in enumerate(self.residuals):
-            self.ono_amd.kernels.synth(t, SEED + i, self.rank)
+            self.ono_amd.kernels.synth(t, SEED + (self.nb - 1 if i == self.pool - 1 else i), self.rank)
         self.torch.cuda.synchronize()
 
-    def measure(self, r) -> tuple[float, dict]:
+    def measure(self, r, phases: bool = True) -> tuple[float, dict]:
         """W + K pull_grads rounds with ring r; (max-over-ranks seconds, timing).
         N = 1: a step is exactly one kernel, so one HIP event pair around the
         timed region gives its average launch duration without per-launch
         events (which add ~6 % to a 130 us stream, tools/stream_variants.hip
         "pull" mode).  N > 1: the timed run has no per-launch events; a second
         run of the same K steps records them to split collectives and kernels
-        for the roofline."""
+        for the roofline (`phases`; not in a plain run)."""
         torch, args, nb = self.torch, self.args, self.nb
         self.refill()
         span = [torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)]
@@ -1059,15 +1084,17 @@ class Runner:
         def on_start():
             span[0].record(self.stream)
 
+        buckets = [self.bucket(i) for i in range(nb)]
+
         def step(i: int) -> None:
-            r.pull_grads_dev(self.residuals[i], self.grad, self.stream)
+            r.pull_grads_dev(buckets[i], self.grad, self.stream)
             if i == nb - 1:
                 span[1].record(self.stream)
 
         el, _ = timed_region(step, args.steps, args.warmup, torch.cuda.synchronize, self.ctl, on_start=on_start)
         r.check()  # an xGMI barrier timeout would make the timed rounds invalid
         span_ms = span[0].elapsed_time(span[1])
-        if self.world == 1:
+        if self.world == 1 or not phases:
             return el, {"kernel_ms": span_ms, "kernels": args.steps, "collective_ms": 0.0, "collectives": 0}
         self.refill()
         timed_region(step, args.steps, args.warmup, torch.cuda.synchronize, self.ctl,
@@ -1076,6 +1103,24 @@ class Runner:
         tim["phases"] = r.timing_phases()
         r.timing(False)
         return el, tim
+
+    DUMP_ELEMS = 1 << 22
+
+    def dump_outputs(self, out_dir: str) -> None:
+        """--dump-outputs: what the last timed step handed back to its caller — the averaged grad bucket
+        and the residual bucket it zeroed — as float32 .npy files.  Buckets above DUMP_ELEMS elements
+        are written as the elements at DUMP_ELEMS sorted indices drawn once from a fixed seed, so two
+        runs with the same arguments write the same elements."""
+        import numpy as np
+        torch = self.torch
+        os.makedirs(out_dir, exist_ok=True)
+        idx = None
+        if self.elems > self.DUMP_ELEMS:
+            pick = np.sort(np.random.default_rng(SEED).integers(0, self.elems, self.DUMP_ELEMS, dtype=np.int64))
+            idx = torch.from_numpy(pick).to("cuda")
+        for name, t in (("grad", self.grad), ("residual", self.bucket(self.nb - 1))):
+            a = (t if idx is None else t.index_select(0, idx)).cpu().numpy()
+            np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
     def verify(self, wire: str) -> dict:
         """Check the last measured step against the exact average: every rank
@@ -1099,7 +1144,7 @@ class Runner:
         over = err > bound
         ratio = float((err / bound.clamp_min(1e-300)).max().item()) if bool(bound.gt(0).any()) else 0.0
         bad = int(over.sum().item())
-        left = int(self.residuals[i].count_nonzero().item())
+        left = int(self.bucket(i).count_nonzero().item())
         del tmp, acc, mag, bound, err, over
         self.torch.cuda.empty_cache()
         ratio, bad, left = self.ctl.max(ratio), int(self.ctl.max(bad)), int(self.ctl.max(left))
@@ -1346,13 +1391,20 @@ def main(argv=None) -> int:
         stream = None
     else:
         run = Runner(torch, ono_amd, args, ctl, world, rank, elems)
-        measure, stream = run.measure, run.stream
+        stream = run.stream
 
-    link = xgmi_link_probe(torch) if (world > 1 and rank == 0 and not dry) else None
+        def measure(r):
+            return run.measure(r, phases=args.full)
+
+    link = xgmi_link_probe(torch) if (args.full and world > 1 and rank == 0 and not dry) else None
     ctl.barrier()
     elapsed, tim = measure(ring)
+    if args.dump_outputs and rank == 0 and not dry:  # (rank 0's buckets)
+        run.dump_outputs(args.dump_outputs)
 
-    extra = {"check": {"ok": True, "dry_run": True} if dry else run.verify(args.wire)}
+    extra = {}
+    if args.full:
+        extra["check"] = {"ok": True, "dry_run": True} if dry else run.verify(args.wire)
     if watchdog is not None:
         watchdog.cancel()
     if world == 1:
@@ -1373,7 +1425,7 @@ def main(argv=None) -> int:
             extra["roofline"]["traffic_provenance"] = (
                 f"committed profile {pmc['source']}@{pmc.get('commit', 'unknown')} "
                 f"({pmc.get('session', 'a builder session')}); not measured in this run")
-    else:
+    elif args.full:  # (it splits the step by phase: the second, event-stamped run of measure)
         extra["roofline"] = nx_roofline(tim, bucket_bytes, elems, world, args.wire, ring.algo, args.steps, elapsed,
                                         link)
 
@@ -1388,6 +1440,12 @@ def main(argv=None) -> int:
         line["config"]["collective"] = "xGMI peer-access kernels over IPC-mapped peer HBM (no RCCL)"
     if world > 1 and args.wire == "f32" and ring.algo in ("auto", "allreduce"):
         line["config"]["allreduce_segments"] = args.segments or "library default (ONO_AR_SEGMENTS or 4)"
+    if not args.full:  # a plain run: the headline alone
+        ring.close()
+        ctl.close()
+        if rank == 0:
+            print(BOX.dump(), flush=True)
+        return 0
     line["deadline"] = {"s": args.deadline, "skipped": []}
     backstop = start_backstop(budget, rank)
 
@@ -1493,7 +1551,7 @@ def main(argv=None) -> int:
                 params = torch.empty(elems, dtype=torch.float32, device="cuda")
                 run.refill()
                 ring.timing(False)
-                el, _ = timed_region(lambda i: ps.step(run.residuals[i], params, stream), args.steps, args.warmup,
+                el, _ = timed_region(lambda i: ps.step(run.bucket(i), params, stream), args.steps, args.warmup,
                                      torch.cuda.synchronize, ctl)
                 ps.close()
                 del params
@@ -1617,7 +1675,7 @@ def xgmi_child_main(args) -> int:
                 ps = ono_amd.ShardedParamServer(ring, np.zeros(elems, np.float32), ono_amd.GradientDescent(0.1))
                 params = torch.empty(elems, dtype=torch.float32, device="cuda")
                 run.refill()
-                el, _ = timed_region(lambda i: ps.step(run.residuals[i], params, run.stream), args.steps,
+                el, _ = timed_region(lambda i: ps.step(run.bucket(i), params, run.stream), args.steps,
                                      args.warmup, torch.cuda.synchronize, ctl)
                 out["xgmi-ps:gd"] = {
                     "value": round(world * elems * 4 * args.steps / el / GIB, 3),

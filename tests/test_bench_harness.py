@@ -196,12 +196,14 @@ def test_nx_line_carries_xgmi_algbw_links_and_phases(algo, wire):
     json.dumps(line)
 
 
-def _bench(args, timeout=120, **env):
+def _bench(args, timeout=120, full=True, **env):
+    """bench.py --dry-run; the legs, the check and the deadline belong to --full."""
     e = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "ONO_BENCH_DEADLINE")}
     e.update(env, HIP_VISIBLE_DEVICES="")
     t0 = time.time()
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--steps", "3", "--warmup", "1",
-                        *args], capture_output=True, text=True, timeout=timeout, env=e, cwd=ROOT)
+                        *(["--full"] if full else []), *args],
+                       capture_output=True, text=True, timeout=timeout, env=e, cwd=ROOT)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     return r, lines, time.time() - t0
 
@@ -294,7 +296,7 @@ def test_under_torchrun_one_gpu_free_launcher_prints_one_line(fail):
         e["ONO_BENCH_DRY_RING_FAIL"] = "1"
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-                        "--gpus", "2", "--dry-run", "--steps", "3", "--warmup", "1", "--deadline", "60"],
+                        "--gpus", "2", "--dry-run", "--full", "--steps", "3", "--warmup", "1", "--deadline", "60"],
                        capture_output=True, text=True, timeout=180, env=e, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -302,3 +304,71 @@ def test_under_torchrun_one_gpu_free_launcher_prints_one_line(fail):
     line = json.loads(lines[0])
     assert line["n_gpus"] == 2 and line["value"] > 0
     assert ("headline_fallback" in line) == fail
+
+
+def test_a_plain_run_prints_the_headline_alone():
+    """Without --full: set up, warm up, K timed steps, the result line — no check, no leg, no deadline."""
+    r, lines, took = _bench(["--dry-leg-s", "60"], full=False)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert len(lines) == 1, r.stdout
+    line = json.loads(lines[0])
+    assert line["metric"] == bench.METRIC and line["unit"] == "GiB/s" and line["dtype"] == "f32"
+    assert line["higher_is_better"] is True and line["value"] > 0
+    assert line["steps"] == 3 and line["warmup"] == 1
+    assert line["ms_per_step"] >= 1.0  # the dry step sleeps 1 ms
+    for key in ("check", "deadline", "host_fed", "tcp_edge", "ps_host_fed", "local_reduce", "path_kernels",
+                "sparse_codec", "copy_ceiling", "cpu_baseline", "xgmi_coresident", "alt_schedules", "size_sweep"):
+        assert key not in line, key
+    assert took < 30  # (a leg would have slept 60 s)
+
+
+def test_two_plain_ranks_print_one_line_without_legs():
+    r, lines, _ = _bench(["--gpus", "2", "--dry-leg-s", "60"], full=False)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert len(lines) == 1, r.stdout
+    line = json.loads(lines[0])
+    assert line["n_gpus"] == 2 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert "alt_schedules" not in line and "size_sweep" not in line and "check" not in line
+
+
+class _FakeTorch:
+    """Runner's bucket pool on the CPU: tensors are their serial numbers."""
+    float32 = "f32"
+
+    class cuda:
+        @staticmethod
+        def current_stream():
+            return None
+
+    def __init__(self):
+        self.made = 0
+
+    def empty(self, *_a, **_k):
+        self.made += 1
+        return self.made - 1
+
+
+@pytest.mark.parametrize("steps,warmup,pool_buckets", [(20, 5, 128), (3, 1, 2), (200, 5, 8), (1, 0, 8), (7, 1, 8)])
+def test_runner_steps_go_round_a_bounded_pool_and_the_last_keeps_its_own_bucket(steps, warmup, pool_buckets,
+                                                                               monkeypatch):
+    """--steps sets the number of timed steps whatever it is: the buckets stay within Runner.POOL_BYTES, every
+    step of a run the pool holds has its own bucket with its own seed (as before), and the last step's bucket,
+    seeded by W + K - 1, is no other step's."""
+    import types
+    elems = 1 << 10
+    monkeypatch.setattr(bench.Runner, "POOL_BYTES", pool_buckets * 4 * elems)
+    t = _FakeTorch()
+    run = bench.Runner(t, None, types.SimpleNamespace(steps=steps, warmup=warmup), bench.Ctl(1, 0), 1, 0, elems)
+    nb = steps + warmup
+    assert run.nb == nb and t.made == min(nb, pool_buckets) + 1  # + the grad bucket
+    order = [run.bucket(i) for i in range(nb)]
+    assert order[-1] not in order[:-1]
+    if nb <= pool_buckets:
+        assert order == list(range(nb))
+    seeds = []
+    run.ono_amd = types.SimpleNamespace(kernels=types.SimpleNamespace(synth=lambda b, seed, rank: seeds.append((b, seed))))
+    run.torch = types.SimpleNamespace(cuda=types.SimpleNamespace(synchronize=lambda: None))
+    run.refill()
+    assert dict(seeds)[order[-1]] == bench.SEED + nb - 1
+    if nb <= pool_buckets:
+        assert seeds == [(i, bench.SEED + i) for i in range(nb)]

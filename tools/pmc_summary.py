@@ -4,8 +4,8 @@ HBM bytes of each kernel (profiles/<round>_pmc_*.json, read by bench.py).
 
 Collection (two separate passes, counters only — MI355X_MICROARCH.md §HBM,
 §rocprofv3 PMC slots: FETCH_SIZE and WRITE_SIZE do not fit one TCC pass):
-  rocprofv3 --pmc FETCH_SIZE --output-format csv -d OUT/fetch -o run -- python3 bench.py ...
-  rocprofv3 --pmc WRITE_SIZE --output-format csv -d OUT/write -o run -- python3 bench.py ...
+  rocprofv3 --pmc FETCH_SIZE --output-format csv -d OUT/fetch -o run -- python3 bench.py --full ...
+  rocprofv3 --pmc WRITE_SIZE --output-format csv -d OUT/write -o run -- python3 bench.py --full ...
 
 gfx950 corrections applied (same guide): counters are in KiB; FETCH_SIZE
 reports exactly half of the bytes of a wide (16 B/lane) coalesced streaming
