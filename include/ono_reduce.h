@@ -106,6 +106,16 @@ int ono_f16_add_encode_zero(uint16_t *out, float *acc, const uint16_t *in, size_
                             void *stream);
 /* gather receive: out = f32(in) / divisor         (worker_ring.rs:200 + :101-105) */
 int ono_f16_decode_scale(float *out, const uint16_t *in, size_t n, float divisor, void *stream);
+/* The settle of a SparseCapable push to a parameter server, stream-ordered
+ * behind the threshold and the stream-ordered drop of the same residual
+ * (ono_cluster_push_grads): Compressor::compress's size rule
+ * (compressor.rs:79-89) and server_cluster.rs:88-96 on the device.  t_dev and
+ * nbytes_dev are device (or host-mapped) words: the push's threshold and the
+ * drop stream's length.  *nbytes_dev <= 2 n (the SparseGrad goes out):
+ * residual[i] = 0 where |residual[i]| >= *t_dev, out16 untouched; otherwise
+ * (the DenseGrad goes out): out16[i] = f16(residual[i]), residual[i] = 0.    */
+int ono_push_settle_f32(uint16_t *out16, float *residual, size_t n, const float *t_dev,
+                        const uint64_t *nbytes_dev, void *stream);
 
 /* The chunk owner's reduction of the DIRECT / XGMI schedules (one fused
  * kernel per round): ins[j] = the slice of chunk c from rank c+j (HOST array
@@ -505,6 +515,20 @@ int ono_store_accumulate_dev(ono_store *store, const float *grad_dev, size_t n);
  * server's CPU decode (handles/worker.rs:82-101) + accumulate, fused.        */
 int ono_store_accumulate_f16(ono_store *store, const uint16_t *grad_f16_host, size_t n);
 int ono_store_accumulate_f16_dev(ono_store *store, const uint16_t *grad_f16_dev, size_t n);
+/* The same from a SparseCapable worker's wire form, the grad_drop stream of a
+ * SparseGrad frame (push_grad, parameter_server.rs:92-107): the server's
+ * WorkerHandle::recv_event arm (handles/worker.rs:102-108) — grad_lift_into
+ * (sparse/protocol.rs:96-144) into a zero-filled gradient — then
+ * Store::accumulate of it.  The stream is lifted on the device into the
+ * store's staging buffer (ono_sparse_lift / _dev on the store's stream), then
+ * the accumulate kernel runs; the WildStore's optimizer sees the lifted zeros
+ * too, so momentum and Adam state decay on unsent positions (wild/shard.rs:
+ * 43-58).  The stream's total_len (its first 8 bytes) must equal the store
+ * length — ONO_E_SIZE otherwise, checked before the lift; a malformed stream
+ * is ONO_E_PROTO with the reference's message; either way the store is left
+ * as it was.  Any well-formed stream is taken, whatever its length.         */
+int ono_store_accumulate_sparse(ono_store *store, const uint8_t *stream_host, size_t nbytes);
+int ono_store_accumulate_sparse_dev(ono_store *store, const uint8_t *stream_dev, size_t nbytes);
 /* Store::update_params (store.rs:93-108): CAS-guarded; a concurrent second
  * caller returns immediately without updating.                              */
 int ono_store_update_params(ono_store *store);
@@ -531,6 +555,88 @@ int ono_sync_step(ono_sync *sync, ono_store *store, const float *grad_host, floa
 /* the same with the gradient as the f16 payload it arrives in (fused decode) */
 int ono_sync_step_f16(ono_sync *sync, ono_store *store, const uint16_t *grad_f16_host, float *params_host,
                       size_t n);
+/* the same with the gradient as a SparseGrad's stream (ono_store_accumulate_sparse);
+ * n = the length of params_host                                             */
+int ono_sync_step_sparse(ono_sync *sync, ono_store *store, const uint8_t *stream_host, size_t nbytes,
+                         float *params_host, size_t n);
+
+/* ===================================================================== */
+/* Parameter-server mode on the TCP edge: the reference's frames            */
+/* ([u64 BE len][u32 BE kind][payload], comms/src/protocol/msg.rs:98-110,   */
+/* 160-191) on the caller's connected sockets (the caller keeps ownership). */
+/* An MI355X server under reference workers, MI355X workers under           */
+/* reference servers, or both.                                               */
+/* ===================================================================== */
+/* The server's task for one worker (ParameterServer::spawn,
+ * parameter_server/src/service/pserver.rs:105-163).  create takes a clone of
+ * the synchronizer (ono_sync_clone) that destroy releases (ono_sync_release:
+ * barrier.rs:30-38); the store is the caller's.  run blocks: it pulls the
+ * parameters and sends them as a Params frame (kind 5, f32 LE), then for every
+ * received frame: a DenseGrad (kinds 1 / 2) takes ono_sync_step_f16 on its
+ * payload, a SparseGrad (kinds 3 / 4) ono_sync_step_sparse; after an is_last
+ * gradient (kinds 2 / 4) run returns ONO_OK without sending parameters, else
+ * it sends the stepped parameters and waits for the next frame.  A gradient
+ * of another length than the store is passed over — no step, no parameters
+ * sent, the next frame awaited (:145-151); a SparseGrad's length is its
+ * total_len, read before the lift, so a malformed stream with a wrong total is
+ * passed over too where the reference reports the lift's error (its lift runs
+ * first).  A malformed stream of the right total is ONO_E_PROTO with the lift's
+ * message.  Any other frame ends the task (:152-155): ONO_E_IO "loss
+ * diverged: NaN or Inf detected" for a non-finite ReportLoss and "Received an
+ * invalid kind byte" for a kind >= 7, else ONO_E_PROTO "invalid message".
+ * Every socket wait watches the abort flag and timeout_s, the longest one send
+ * or one wait for a frame may take (<= 0: 600 s): ONO_E_ABORTED, ONO_E_IO.    */
+typedef struct ono_server_task ono_server_task;
+int ono_server_task_create(ono_server_task **out, ono_sync *sync, ono_store *store, int fd, double timeout_s);
+int ono_server_task_run(ono_server_task *task);
+/* from another thread: a running (or later) run returns ONO_E_ABORTED.  A run
+ * waiting inside a BarrierSync step returns once the barrier lets it go.     */
+int ono_server_task_abort(ono_server_task *task);
+int ono_server_task_destroy(ono_server_task *task);
+
+/* The worker's side: ServerClusterManager (worker/src/middlewares/
+ * server_cluster.rs:7-105) with its buckets in HBM.  Server j holds sizes[j]
+ * >= 1 parameters behind the socket fds[j]; params, grad and residual are one
+ * contiguous server-major allocation per kind (zeroed), so server j's bucket
+ * starts sizes[0] + ... + sizes[j-1] values after server 0's.               */
+typedef struct ono_cluster ono_cluster;
+int ono_cluster_create(ono_cluster **out, int nservers, const size_t *sizes, const int *fds, int device,
+                       double timeout_s);
+/* The serializer of every server handle: SparseCapable{ratio} (ratio in
+ * (0, 1]) or Base (0, the default).  Each handle's default sampler starts its
+ * own stream at `seed` (ParamServerHandle::enable_sparse_capability).        */
+int ono_cluster_set_sparse(ono_cluster *cluster, float ratio, uint64_t seed);
+/* the threshold sampler of one handle (as ono_ring_set_sampler; NULL = default) */
+int ono_cluster_set_sampler(ono_cluster *cluster, int server, ono_sample_fn fn, void *ctx);
+/* device pointers to server j's buckets (NULL for a bad handle or index) */
+float *ono_cluster_params(ono_cluster *cluster, int server);
+float *ono_cluster_grad(ono_cluster *cluster, int server);
+float *ono_cluster_residual(ono_cluster *cluster, int server);
+size_t ono_cluster_size(const ono_cluster *cluster, int server);
+/* pull_params (:52-76): one Params frame per server, in server order, into the
+ * params buckets; blocking.  Another frame -> ONO_E_IO "Expected params from
+ * server j" (parameter_server.rs:75-78); another length -> ONO_E_SIZE.        */
+int ono_cluster_pull_params(ono_cluster *cluster);
+/* ParamManager::acc_residual over every server: residual += grad, one launch
+ * on `stream`; the next push is ordered after it.                            */
+int ono_cluster_acc_residual(ono_cluster *cluster, void *stream);
+/* push_grads (:85-104): every server's residual through its handle's
+ * Compressor::compress (compressor.rs:71-98), in server order.  Base: the
+ * DenseGrad of f16(residual) (kind 1, or 2 when is_last), residual = 0.
+ * SparseCapable: t = calculate_threshold(residual, r) and the grad_drop stream;
+ * a stream of at most 2 bytes per value goes out as a SparseGrad (kind 3 / 4)
+ * and residual = 0 where |residual| >= t, else the DenseGrad goes out and the
+ * whole residual is zeroed.  The device work of all servers is enqueued back
+ * to back on the cluster's stream (threshold, stream-ordered drop,
+ * ono_push_settle_f32) and waited for once; then the frames are sent.  A
+ * server whose worst-case stream does not fit the cluster's pinned frames
+ * (4 MiB) is encoded in HBM and comes down after that wait, at its exact
+ * length, behind one more wait.  Writers of the residual on other streams
+ * than acc_residual's must have completed.  Blocking.                        */
+int ono_cluster_push_grads(ono_cluster *cluster, int is_last);
+/* from another thread: a waiting (or later) pull / push returns ONO_E_ABORTED */
+int ono_cluster_abort(ono_cluster *cluster);
+int ono_cluster_destroy(ono_cluster *cluster);
 
 /* DynBarrier (synchronization/dyn_barrier.rs:47-106), exposed for the host tests */
 typedef struct ono_barrier ono_barrier;

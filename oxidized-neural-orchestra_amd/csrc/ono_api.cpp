@@ -96,6 +96,13 @@ int ono_f16_encode_zero(uint16_t *out, float *chunk, size_t n, void *stream) {
     ONO_LAUNCH(launch_encode_zero<uint16_t>(out, chunk, n, S(stream)));
 }
 
+int ono_push_settle_f32(uint16_t *out16, float *residual, size_t n, const float *t_dev, const uint64_t *nbytes_dev,
+                        void *stream) {
+    if (n && (!out16 || !residual)) return set_error(ONO_E_ARG, "NULL pointer");
+    if (!t_dev || !nbytes_dev) return set_error(ONO_E_ARG, "NULL pointer");
+    ONO_LAUNCH(launch_push_settle(out16, residual, n, t_dev, nbytes_dev, S(stream)));
+}
+
 int ono_f16_decode_add(float *acc, const uint16_t *in, size_t n, void *stream) {
     if (n && (!acc || !in)) return set_error(ONO_E_ARG, "NULL pointer");
     ONO_LAUNCH(launch_decode_add<uint16_t>(acc, in, n, S(stream)));

@@ -74,6 +74,14 @@ int sparse_threshold_dev(float *t_dev, const float *g, size_t n, const uint32_t 
 int sparse_drop_tdev(uint8_t *buf, size_t cap, size_t *nbytes, const float *g, size_t n, const float *t_dev,
                      hipStream_t s);
 hipError_t launch_sparse_mask_tdev(float *g, size_t n, const float *t_dev, int zero_kept, hipStream_t s);
+// ono_sparse_drop_async with the threshold read at t_dev: nothing waits on the host, the length lands in
+// *nbytes_dev (cap = ono_sparse_max_bytes(n)) — the parameter-server push (ono_ps_tcp.cpp)
+int sparse_drop_tdev_async(uint8_t *buf, size_t cap, uint64_t *nbytes_dev, const float *g, size_t n, const float *t_dev,
+                           hipStream_t s);
+// the push's settle (ono_kernels.hip PushSettleOp): *nbytes_dev <= 2 n -> residual = 0 where |residual| >= *t_dev;
+// else out16 = f16(residual), residual = 0
+hipError_t launch_push_settle(uint16_t *out16, float *residual, size_t n, const float *t_dev, const uint64_t *nbytes_dev,
+                              hipStream_t s);
 // one launch: dst[0, k) += src (add) or = src (copy), and the mask of mg[0, mn) (sp_mask's zero_kept form)
 // with the threshold at t_dev — the SparseCapable hop's work after its exchange; keys != NULL: also the keys
 // |dst[idx[j]]| of the next push's sample (dst, L values), idx bucketed by 256-value blocks (offs: L / 256 + 1)

@@ -185,6 +185,14 @@ bool wide_blocks() {
     return v;
 }
 
+// Ops whose branch hangs on words another launch left in device memory read them once per workgroup, before
+// any element, in begin() (PushSettleOp: the push's threshold and its stream's length).
+template <class Op, class = void> struct HasBegin : std::false_type {};
+template <class Op> struct HasBegin<Op, std::void_t<decltype(std::declval<Op &>().begin())>> : std::true_type {};
+template <class Op> __device__ __forceinline__ void begin_wave(Op &op) {
+    if constexpr (HasBegin<Op>::value) op.begin();
+}
+
 // LOOP = false: the grid covers every vector (the one-shot grid), so no loop
 // at all — one guarded vector per lane (dec 2.5 %, sum8 1 % faster than the
 // loop form, tools/skeleton_variants.hip; profiles/r02_skeleton_variants.txt).
@@ -192,6 +200,7 @@ template <class Op, bool LOOP, int B = block_of<Op>()>
 __global__ __launch_bounds__(B) void ew_kernel(Op op, size_t head, size_t nvec, size_t n) {
     const size_t tid = (size_t)blockIdx.x * B + threadIdx.x;
     const size_t tail0 = head + 4 * nvec;
+    begin_wave(op);
     if (tid < head) op.scalar(tid);
     if (tid < n - tail0) op.scalar(tail0 + tid);
     if constexpr (LOOP) {
@@ -207,6 +216,7 @@ __global__ __launch_bounds__(B) void ew_kernel(Op op, size_t head, size_t nvec, 
 template <class Op, int B = block_of<Op>()>
 __global__ __launch_bounds__(B) void ew_scalar_kernel(Op op, size_t n) {
     const size_t stride = (size_t)gridDim.x * B;
+    begin_wave(op);
     for (size_t i = (size_t)blockIdx.x * B + threadIdx.x; i < n; i += stride) op.scalar(i);
     finish_wave(op);
 }
@@ -605,6 +615,53 @@ template <class W> struct EncodeZeroOp {
     __device__ __forceinline__ void store(size_t i, R x) const {
         st_sc1((WV *)(out + i), Wire<W>::enc4(x));
         st_sc1((f4 *)(chunk + i), f4{0.0f, 0.0f, 0.0f, 0.0f});
+    }
+};
+
+// The settle of a SparseCapable push to a parameter server (ono_cluster_push_grads): Compressor::compress's
+// size rule (compressor.rs:79-89) and the bookkeeping of server_cluster.rs:88-96, on the device, so that the
+// threshold, the drop and this launch run back to back with no host wait between them.  The drop left its
+// stream's length at *nbytes_dev and the threshold is at *t_dev; limit = 2 n, the chunk's f16 payload.
+//   *nbytes_dev <= limit  the SparseGrad goes out: residual = 0 where |residual| >= t (NaN never sent), out
+//                         untouched — a read of the residual and a store of the vectors that change;
+//   else                  the DenseGrad goes out: out = f16(residual), residual = 0 — EncodeZeroOp's stream,
+//                         with its `nt sc1` stores and its occupancy cap.
+// The branch is the same for every lane of the launch (begin() reads both words once per workgroup).
+struct PushSettleOp {
+    uint16_t *out;
+    float *res;
+    const float *t_dev;
+    const uint64_t *nbytes_dev;
+    uint64_t limit;
+    float t;
+    bool dense;
+    __host__ int occ() const { return 24; }
+    typedef f4 R;
+    __device__ __forceinline__ void begin() {
+        t = *t_dev;
+        dense = *nbytes_dev > limit;
+    }
+    __device__ __forceinline__ void scalar(size_t i) const {
+        const float x = res[i];
+        if (dense) {
+            out[i] = to_f16(x);
+            res[i] = 0.0f;
+        } else if (fabsf(x) >= t) {
+            res[i] = 0.0f;
+        }
+    }
+    // one plain load ahead of the branch (the sparse form rewrites part of the lines it reads: the skeleton's
+    // note on ldn; a load per branch is merged into this one by the compiler anyway)
+    __device__ __forceinline__ R load(size_t i) const { return ld((const f4 *)(res + i)); }
+    __device__ __forceinline__ void store(size_t i, R x) const {
+        if (dense) {
+            st_sc1((h4 *)(out + i), Wire<uint16_t>::enc4(x));
+            st_sc1((f4 *)(res + i), f4{0.0f, 0.0f, 0.0f, 0.0f});
+            return;
+        }
+        const bool k0 = fabsf(x.x) >= t, k1 = fabsf(x.y) >= t, k2 = fabsf(x.z) >= t, k3 = fabsf(x.w) >= t;
+        if (k0 | k1 | k2 | k3)
+            st((f4 *)(res + i), f4{k0 ? 0.0f : x.x, k1 ? 0.0f : x.y, k2 ? 0.0f : x.z, k3 ? 0.0f : x.w});
     }
 };
 
@@ -1010,6 +1067,11 @@ hipError_t launch_decode_scale(float *out, const W *in, size_t n, float divisor,
 }
 template <class W> hipError_t launch_encode_zero(W *out, float *chunk, size_t n, hipStream_t s, KernelDone *done) {
     return launch_ew(EncodeZeroOp<W>{out, chunk}, n, {wph(out), phase_of(chunk, 4)}, s, done);
+}
+hipError_t launch_push_settle(uint16_t *out16, float *residual, size_t n, const float *t_dev, const uint64_t *nbytes_dev,
+                              hipStream_t s) {
+    return launch_ew(PushSettleOp{out16, residual, t_dev, nbytes_dev, 2 * (uint64_t)n, 0.0f, false}, n,
+                     {wph(out16), phase_of(residual, 4)}, s);
 }
 template <class W> hipError_t launch_decode_add(float *acc, const W *in, size_t n, hipStream_t s) {
     return launch_ew(DecodeAddOp<W>{acc, in}, n, {phase_of(acc, 4), wph(in)}, s);

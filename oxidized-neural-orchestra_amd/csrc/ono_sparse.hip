@@ -4445,6 +4445,16 @@ int sparse_drop_tdev(uint8_t *buf, size_t cap, size_t *nbytes, const float *g, s
     if (rc) return rc;
     return drop_launch(buf, cap, nbytes, nullptr, g, n, 0.0f, s, t_dev);
 }
+int sparse_drop_tdev_async(uint8_t *buf, size_t cap, uint64_t *nbytes_dev, const float *g, size_t n, const float *t_dev,
+                           hipStream_t s) {
+    if (!nbytes_dev || !t_dev) return set_error(ONO_E_ARG, "NULL argument");
+    int rc = drop_args(g, n, buf, cap);
+    if (rc) return rc;
+    if (cap < ono_sparse_max_bytes(n))
+        return set_error(ONO_E_SIZE, "the stream-ordered drop needs the worst-case buffer (%zu bytes, have %zu)",
+                         ono_sparse_max_bytes(n), cap);
+    return drop_launch(buf, cap, nullptr, nbytes_dev, g, n, 0.0f, s, t_dev);
+}
 hipError_t launch_hop_post(float *dst, const float *src, size_t k, int add, float *mg, size_t mn, const float *t_dev,
                            int zero_kept, hipStream_t s, size_t L, const uint32_t *idx, const uint32_t *offs,
                            uint32_t *keys) {

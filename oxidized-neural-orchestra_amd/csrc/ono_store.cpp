@@ -160,8 +160,57 @@ static int accumulate_f16(ono_store *st, const uint16_t *grad, size_t n, hipMemc
     return ONO_OK;
 }
 
+// The SparseGrad arm of the receive (handles/worker.rs:102-108 feeding
+// Store::accumulate): grad_lift_into on the device into the staging buffer —
+// on the store's stream and under st->mu, so the lift's per-stream scratch has
+// one caller — then the f32 accumulate's own tail.  Nothing is added from
+// inside the lift: a refuted tier may have written part of its output, which
+// only ever reaches the staging buffer.
+static int accumulate_sparse(ono_store *st, const uint8_t *buf, size_t nbytes, bool dev) {
+    if (!st || (!buf && nbytes)) return set_error(ONO_E_ARG, "NULL argument");
+    if (nbytes < 8) return set_error(ONO_E_PROTO, "The given sparse buffer is smaller than TOTAL_LEN_SIZE");
+    std::lock_guard<std::mutex> lk(st->mu);
+    DeviceGuard g(st->device);
+    hipStream_t s = st->stream;
+    uint8_t head[8];
+    if (dev) {
+        ONO_HIP(hipMemcpyAsync(head, buf, 8, hipMemcpyDeviceToHost, s));
+        ONO_HIP(hipStreamSynchronize(s));
+    } else {
+        memcpy(head, buf, 8);
+    }
+    uint64_t total = 0;
+    for (int q = 0; q < 8; q++) total |= (uint64_t)head[q] << (8 * q);
+    if (total != st->nparams)
+        return set_error(ONO_E_SIZE, "gradient of %llu elements, store of %zu", (unsigned long long)total, st->nparams);
+    const size_t n = st->nparams;
+    size_t got = 0;
+    int rc = dev ? ono_sparse_lift_dev(st->scratch, n, &got, buf, nbytes, s)
+                 : ono_sparse_lift(st->scratch, n, &got, buf, nbytes, s);
+    if (rc) return rc;
+    if (n == 0) return ONO_OK;
+    if (st->kind == ONO_STORE_WILD) {
+        adam_advance(st);
+        OptLaunch o = st->opt;
+        o.nworkers = 1.0f;
+        o.plus_zero = false;
+        ONO_HIP(launch_opt_update(o, st->scratch, st->params, st->v, st->s, n, false, s));
+    } else {
+        int active = st->active_idx.load(std::memory_order_acquire);
+        ONO_HIP(launch_acc(st->grads[active], st->scratch, n, s, true));
+    }
+    ONO_HIP(hipStreamSynchronize(s));
+    return ONO_OK;
+}
+
 int ono_store_accumulate(ono_store *st, const float *grad, size_t n) {
     return accumulate(st, grad, n, hipMemcpyHostToDevice);
+}
+int ono_store_accumulate_sparse(ono_store *st, const uint8_t *buf, size_t nbytes) {
+    return accumulate_sparse(st, buf, nbytes, false);
+}
+int ono_store_accumulate_sparse_dev(ono_store *st, const uint8_t *buf, size_t nbytes) {
+    return accumulate_sparse(st, buf, nbytes, true);
 }
 int ono_store_accumulate_dev(ono_store *st, const float *grad, size_t n) {
     return accumulate(st, grad, n, hipMemcpyDeviceToDevice);
@@ -323,10 +372,13 @@ int ono_sync_release(ono_sync *s) {
     return ONO_OK;
 }
 
-static int sync_step(ono_sync *s, ono_store *st, const void *grad, bool f16, float *params, size_t n) {
+enum GradForm { GRAD_F32, GRAD_F16, GRAD_SPARSE };
+static int sync_step(ono_sync *s, ono_store *st, const void *grad, GradForm form, size_t nbytes, float *params,
+                     size_t n) {
     if (!s || !st) return set_error(ONO_E_ARG, "NULL argument");
-    int rc = f16 ? ono_store_accumulate_f16(st, static_cast<const uint16_t *>(grad), n)
-                 : ono_store_accumulate(st, static_cast<const float *>(grad), n);
+    int rc = form == GRAD_F16      ? ono_store_accumulate_f16(st, static_cast<const uint16_t *>(grad), n)
+             : form == GRAD_SPARSE ? ono_store_accumulate_sparse(st, static_cast<const uint8_t *>(grad), nbytes)
+                                   : ono_store_accumulate(st, static_cast<const float *>(grad), n);
     if (rc) return rc;
     if (s->kind == ONO_SYNC_BARRIER) {
         int urc = ONO_OK;
@@ -340,10 +392,13 @@ static int sync_step(ono_sync *s, ono_store *st, const void *grad, bool f16, flo
 }
 
 int ono_sync_step(ono_sync *s, ono_store *st, const float *grad, float *params, size_t n) {
-    return sync_step(s, st, grad, false, params, n);
+    return sync_step(s, st, grad, GRAD_F32, 0, params, n);
 }
 int ono_sync_step_f16(ono_sync *s, ono_store *st, const uint16_t *grad, float *params, size_t n) {
-    return sync_step(s, st, grad, true, params, n);
+    return sync_step(s, st, grad, GRAD_F16, 0, params, n);
+}
+int ono_sync_step_sparse(ono_sync *s, ono_store *st, const uint8_t *stream, size_t nbytes, float *params, size_t n) {
+    return sync_step(s, st, stream, GRAD_SPARSE, nbytes, params, n);
 }
 
 }  // extern "C"

@@ -19,6 +19,7 @@ from .ring import (DeviceOptimizer, ParamManager, WorkerRingManager, local_ring_
 from .store import (Adam, AddOptimizer, BarrierSync, BlockingStore, DynBarrier, GradientDescent,
                     GradientDescentWithMomentum, NoBlockingSync, WildStore, shard_size_for)
 from .ps import ShardedParamServer
+from .ps_tcp import ServerClusterManager, ServerTask
 
 lib()  # fail loudly at import when the native library is missing
 
@@ -28,5 +29,5 @@ __all__ = [
     "local_ring_pull_grads", "unique_id", "Adam", "AddOptimizer", "BarrierSync", "BlockingStore",
     "DynBarrier", "GradientDescent", "GradientDescentWithMomentum", "NoBlockingSync", "WildStore",
     "shard_size_for", "ShardedParamServer", "worker_event_check", "xgmi_pool_release", "xgmi_pool_stats",
-    "xgmi_pool_close_imports", "xgmi_pool_free_exports",
+    "xgmi_pool_close_imports", "xgmi_pool_free_exports", "ServerClusterManager", "ServerTask",
 ]

@@ -177,6 +177,26 @@ _SIGS = {
     "ono_sync_release": (_i, [_vp]),
     "ono_sync_step": (_i, [_vp, _vp, _fp, _fp, _sz]),
     "ono_sync_step_f16": (_i, [_vp, _vp, _vp, _fp, _sz]),
+    "ono_push_settle_f32": (_i, [_vp, _fp, _sz, _vp, _vp, _vp]),
+    "ono_store_accumulate_sparse": (_i, [_vp, _vp, _sz]),
+    "ono_store_accumulate_sparse_dev": (_i, [_vp, _vp, _sz]),
+    "ono_sync_step_sparse": (_i, [_vp, _vp, _vp, _sz, _fp, _sz]),
+    "ono_server_task_create": (_i, [C.POINTER(C.c_void_p), _vp, _vp, _i, C.c_double]),
+    "ono_server_task_run": (_i, [_vp]),
+    "ono_server_task_abort": (_i, [_vp]),
+    "ono_server_task_destroy": (_i, [_vp]),
+    "ono_cluster_create": (_i, [C.POINTER(C.c_void_p), _i, C.POINTER(C.c_size_t), C.POINTER(C.c_int), _i, C.c_double]),
+    "ono_cluster_set_sparse": (_i, [_vp, C.c_float, _u64]),
+    "ono_cluster_set_sampler": (_i, [_vp, _i, _vp, _vp]),
+    "ono_cluster_params": (C.c_void_p, [_vp, _i]),
+    "ono_cluster_grad": (C.c_void_p, [_vp, _i]),
+    "ono_cluster_residual": (C.c_void_p, [_vp, _i]),
+    "ono_cluster_size": (_sz, [_vp, _i]),
+    "ono_cluster_pull_params": (_i, [_vp]),
+    "ono_cluster_acc_residual": (_i, [_vp, _vp]),
+    "ono_cluster_push_grads": (_i, [_vp, _i]),
+    "ono_cluster_abort": (_i, [_vp]),
+    "ono_cluster_destroy": (_i, [_vp]),
     "ono_barrier_create": (_i, [C.POINTER(C.c_void_p), _sz]),
     "ono_barrier_destroy": (_i, [_vp]),
     "ono_barrier_wait_with": (_i, [_vp, LEADER_FN, _vp]),

@@ -128,6 +128,23 @@ def f16_decode_scale(out: torch.Tensor, h: torch.Tensor, divisor: float, stream=
     return out
 
 
+def push_settle(out16: torch.Tensor, residual: torch.Tensor, t_dev: torch.Tensor, nbytes_dev: torch.Tensor,
+                stream=None) -> torch.Tensor:
+    """The settle of a SparseCapable push to a parameter server (compressor.rs:79-89 +
+    server_cluster.rs:88-96), reading the threshold (one float32) and the drop stream's
+    length (one 8-byte integer) from device memory: length <= 2 n -> residual = 0 where
+    |residual| >= t, out16 untouched; else out16 = f16(residual), residual = 0."""
+    if out16.numel() != residual.numel():
+        raise ValueError("length mismatch")
+    if not (t_dev.is_cuda and t_dev.dtype == torch.float32 and t_dev.numel() >= 1):
+        raise ValueError("t_dev: a float32 device tensor")
+    if not (nbytes_dev.is_cuda and nbytes_dev.element_size() == 8 and nbytes_dev.numel() >= 1):
+        raise ValueError("nbytes_dev: a 64-bit integer device tensor")
+    call("ono_push_settle_f32", u16_ptr(out16), f32_ptr(residual), residual.numel(), t_dev.data_ptr(),
+         nbytes_dev.data_ptr(), stream_handle(stream))
+    return residual
+
+
 def synth(out: torch.Tensor, seed: int, rank: int, offset: int = 0, stream=None) -> torch.Tensor:
     """Fill with the §8(d) synthetic gradient distribution (bit-identical to the oracle's)."""
     call("ono_synth_f32", f32_ptr(out), out.numel(), int(seed), int(rank), int(offset), stream_handle(stream))

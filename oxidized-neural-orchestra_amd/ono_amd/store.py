@@ -106,6 +106,23 @@ class _Store:
             raise ValueError("host payload must be uint16 (f16 bit patterns) or float16")
         call("ono_store_accumulate_f16", self._h, h.ctypes.data if h.size else None, h.size)
 
+    def accumulate_sparse(self, stream) -> None:
+        """accumulate() from a SparseCapable worker's wire form: the grad_drop
+        stream of a SparseGrad frame (bytes, a uint8 array, or a uint8 CUDA
+        tensor), lifted on the device (grad_lift_into) and accumulated.  The
+        stream's total_len must be the store's length (SizeMismatch); a
+        malformed stream raises InvalidWorkerEvent with the reference's message."""
+        if isinstance(stream, torch.Tensor):
+            if stream.dtype != torch.uint8 or not stream.is_cuda or not stream.is_contiguous():
+                raise ValueError("device stream must be a contiguous uint8 CUDA tensor")
+            call("ono_store_accumulate_sparse_dev", self._h, stream.data_ptr(), stream.numel())
+            return
+        b = np.ascontiguousarray(np.frombuffer(stream, dtype=np.uint8) if isinstance(stream, (bytes, bytearray))
+                                 else stream)
+        if b.dtype != np.uint8:
+            raise ValueError("host stream must be bytes or a uint8 array")
+        call("ono_store_accumulate_sparse", self._h, b.ctypes.data if b.size else None, b.size)
+
     def update_params(self) -> None:
         call("ono_store_update_params", self._h)
 
@@ -211,6 +228,17 @@ class _Sync:
             raise ValueError("params must be a contiguous float32 array")
         call("ono_sync_step_f16", self._h, store._h, h.ctypes.data if h.size else None,
              params.ctypes.data if params.size else None, h.size)
+
+    def step_sparse(self, store: _Store, stream, params: np.ndarray) -> None:
+        """step() with the gradient as a SparseGrad's grad_drop stream (bytes or a uint8 array)."""
+        b = np.ascontiguousarray(np.frombuffer(stream, dtype=np.uint8) if isinstance(stream, (bytes, bytearray))
+                                 else stream)
+        if b.dtype != np.uint8:
+            raise ValueError("stream must be bytes or a uint8 array")
+        if params.dtype != np.float32 or not params.flags.c_contiguous:
+            raise ValueError("params must be a contiguous float32 array")
+        call("ono_sync_step_sparse", self._h, store._h, b.ctypes.data if b.size else None, b.size,
+             params.ctypes.data if params.size else None, params.size)
 
 
 class BarrierSync(_Sync):
